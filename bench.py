@@ -16,7 +16,7 @@ share of it: `--geometry fuselage --patches 16 8 --nel 53 --degree 4`.
 At N = 1 the default run also adds `device_solver` (not part of `value`): the factorisation and the solves of the K it has just assembled -- the other nine tenths of a Newton
 step (`--no-solver` skips it).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--geometry shell|fuselage] [--patches NX NY] [--nel E] [--degree P]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--geometry shell|fuselage] [--patches NX NY] [--nel E] [--degree P] [--dump-outputs DIR]
 N > 1:  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -118,7 +118,44 @@ def parse_args(argv=None):
     ap.add_argument("--no-secondary", action="store_true", help="N = 1, default workload: do not add the C5 record")
     ap.add_argument("--no-solver", action="store_true", help="N = 1, default workload: do not add the device_solver record (factorisation / solves of this K)")
     ap.add_argument("--full-pass-only", action="store_true", help="skip the apply_linear and Newton-pass legs (PMC passes: every launch belongs to a full pass)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+class _Buf:
+    """Zero-copy view of a float64 device buffer of the library for torch.as_tensor(..., device="cuda")."""
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (ptr, False), "version": 2}
+
+
+DUMP_MAX_ENTRIES = 1 << 20     # per array (8 MB of float64): the at most seven arrays stay under 64 MB
+DUMP_SEED = 20241008
+
+
+def dump_outputs(path, torch, D, R_glob=None):
+    """The arrays a caller of the timed path receives from its last step, read from the library's device buffers: the residual (`residual`), the CSR values
+    of K, dR/dCP_0..2 and dR/dh in the layouts of D.pattern (`K`, `dRdCP0` .. `dRdCP2`, `dRdh`) and, with the exchange, the all-gathered global residual
+    (`residual_global`).  An array longer than DUMP_MAX_ENTRIES is replaced by its entries at DUMP_MAX_ENTRIES sorted indices drawn without replacement by
+    numpy.random.default_rng(DUMP_SEED) from its length alone, so that two builds are compared at the same entries."""
+    from goldfish_amd import _lib
+    os.makedirs(path, exist_ok=True)
+    arrays = {"residual": torch.as_tensor(_Buf(_lib.lib().gf_device_ptr(D.h, _lib.BUF_R), D.ndof), device="cuda")}
+    for name, buf, mat in (("K", _lib.BUF_VAL_K, _lib.MAT_K), ("dRdCP0", _lib.BUF_VAL_C0, _lib.MAT_DRDCP0), ("dRdCP1", _lib.BUF_VAL_C1, _lib.MAT_DRDCP1),
+                           ("dRdCP2", _lib.BUF_VAL_C2, _lib.MAT_DRDCP2), ("dRdh", _lib.BUF_VAL_H, _lib.MAT_DRDH)):
+        arrays[name] = torch.as_tensor(_Buf(_lib.lib().gf_device_ptr(D.h, buf), _lib.lib().gf_nnz(D.h, mat)), device="cuda")
+    if R_glob is not None:
+        arrays["residual_global"] = R_glob
+    D.sync()
+    torch.cuda.synchronize()
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ENTRIES:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ENTRIES, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float64, copy=False))
 
 
 def git_head():
@@ -214,9 +251,6 @@ def measure(args, torch, dist, rank, local_rank, world):
     n_gp_total = int(sum(p.nel[0] * p.nel[1] * (p.p + 1) * (p.q + 1) for p in spec.patches))
 
     # zero-copy torch view of the residual buffer for the RCCL exchange
-    class _Buf:
-        def __init__(self, ptr, n):
-            self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<f8", "data": (ptr, False), "version": 2}
     rehearse = os.environ.get("GF_BENCH_REHEARSE") == "1"
     exchange = world > 1 or os.environ.get("GF_BENCH_FORCE_EXCHANGE") == "1"     # the env switch rehearses the N>1 code path on one GPU
     R_loc = torch.as_tensor(_Buf(_lib.lib().gf_device_ptr(D.h, _lib.BUF_R), A.ndof), device="cuda") if exchange else None
@@ -241,20 +275,27 @@ def measure(args, torch, dist, rank, local_rank, world):
             dist.barrier()
             torch.cuda.synchronize()
 
-    for _ in range(args.warmup):
+    for i in range(args.warmup):
+        if i == args.warmup - 1:        # the last warm-up step counts the element-kernel launches of one step
+            fence()
+            D.kernel_ms()
         step()
     fence()
-    D.kernel_ms()                       # reset the HIP-event accumulator
+    _, warm_launches = D.kernel_ms()    # (also resets the HIP-event accumulator)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
     fence()
     dt = time.perf_counter() - t0
-    kern_ms, kern_n = D.kernel_ms()
-    kern_ms_step = kern_ms * kern_n / max(args.steps, 1)      # element-kernel time per step (a step may launch it in chunks)
+    kern_ms, kern_n = D.kernel_ms()     # mean over the last <= 64 launches (the library keeps 64 event pairs), and their number
+    # element-kernel time per step (a step may launch it in chunks); past 64 launches the count per step is the warm-up step's
+    launches_per_step = warm_launches if kern_n >= 64 and warm_launches > 0 else kern_n / args.steps
+    kern_ms_step = kern_ms * launches_per_step
     if exchange:       # the exchanged global residual must equal the library's own copy of the owned rows
         rows = shard.owned_rows_global(3)
         assert np.array_equal(R_glob[torch.from_numpy(rows).cuda()].cpu().numpy(), D.residual()[:rows.size])
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, D, R_glob)
     # the HBM-bound phase of the path: apply_linear = block-CSR SpMV on the assembled K
     # (DispImOpeartion.apply_linear_fwd, disp_imop.py:58-72), device pointers, HIP events on torch's stream are
     # not used: the library's own stream is timed by wall clock around a synchronised batch
@@ -329,7 +370,7 @@ def measure(args, torch, dist, rank, local_rank, world):
             "roofline": {"bound": "hbm", "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                          "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": kern_ms_step, "launches_timed": kern_n,
-                         "launches_per_step": kern_n / max(args.steps, 1), "step_traffic_all_kernels": step_traffic,
+                         "launches_per_step": launches_per_step, "step_traffic_all_kernels": step_traffic,
                          "traffic_source": traffic_source, "timing": "HIP events on the library's stream around every launch of the element kernel(s), this run"},
             "roofline_fp64": {"bound": "fp64 (v_mfma_f64 + FP64 VALU share one pipe)" if mfma else "fp64-valu", "kernel": kname,
                               "achieved": ALG_FLOP_PER_GP[p] * n_gp_local / (kern_ms_step * 1e-3) / 1e12 if kern_ms_step > 0 else 0.0,

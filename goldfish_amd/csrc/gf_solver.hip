@@ -1578,7 +1578,9 @@ struct gfs_handle {
     std::vector<std::vector<int>> sub;       // sub[s]: fronts of the subtrees assigned to stream s, in post-order
     std::vector<int> top;                    // the remaining fronts, in post-order
     // the sweeps are ~1e5 small launches with a fixed structure: captured once into HIP graphs (all streams), replayed per factorisation / substitution
-    hipGraphExec_t g_factor = nullptr, g_solve = nullptr; bool use_graph = true;
+    // off by default (GF_SOLVER_GRAPH=1 turns it on): the first captured nested-dissection solve -- the fork / join ladders of its side streams -- ends in a SIGSEGV
+    // on a thread inside the HIP runtime (ROCm 7.2), also with a 1 GB stack; direct launches give the same results
+    hipGraphExec_t g_factor = nullptr, g_solve = nullptr; bool use_graph = false;
     std::map<void*, int> graph_calls; int graph_after = 3;        // direct launches for the first graph_after calls of every sweep (GF_SOLVER_GRAPH_AFTER)
     // partial handle (gfs_create_nd_partial: a sub-forest of the elimination tree -- a rank's own subtrees, or the top of the tree above stub fronts that stand for the
     // subtrees of other ranks): Schur complements of stub fronts come from device buffers (stub_src, copied in by gfs_refactor), the sweeps run in halves

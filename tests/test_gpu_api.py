@@ -181,16 +181,35 @@ def test_energy_and_volume_comp_partials(var_thickness):
         assert max(errs.values()) < 1e-6, (Comp.__name__, errs)
 
 
-def _rank_worker(rank, world, port, q, backend="gloo"):
+def _init_ranks(rank, world, port, backend):
+    """Process group of one rank of a multi-process test; returns the rank's GPU.  "gloo": every rank on GPU 0.  "nccl" (= RCCL): one GPU per rank.
+    "nccl-one-gpu": RCCL with every rank on GPU 0 (a one-GPU box).  RCCL refuses two ranks of one host on one GPU, so each rank names a host of its own
+    (NCCL_HOSTID) and the ranks connect through RCCL's socket transport over the loopback interface instead of shared memory or peer access."""
     import torch
     import torch.distributed as dist
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dev = rank if backend == "nccl" else 0               # nccl (= RCCL): one GPU per rank; gloo: every rank on GPU 0
-    if backend == "nccl":
-        torch.cuda.set_device(dev)
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev))
-    else:
+    if backend == "gloo":
         dist.init_process_group("gloo", rank=rank, world_size=world)
+        return 0
+    dev = rank if backend == "nccl" else 0
+    if backend == "nccl-one-gpu":
+        os.environ.update(NCCL_HOSTID="goldfish-test-rank-%d" % rank, NCCL_SOCKET_IFNAME="lo", NCCL_IB_DISABLE="1")
+    torch.cuda.set_device(dev)
+    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev))
+    return dev
+
+
+def _rccl_world(ranks):
+    """(world, backend) of a test over RCCL: min(device_count, ranks) ranks with a GPU each, or two ranks sharing the GPU of a one-GPU box."""
+    import torch
+    n = torch.cuda.device_count()                         # does not initialise the GPU in this process
+    return (min(n, ranks), "nccl") if n >= 2 else (2, "nccl-one-gpu")
+
+
+def _rank_worker(rank, world, port, q, backend="gloo"):
+    import torch
+    import torch.distributed as dist
+    dev = _init_ranks(rank, world, port, backend)
     from goldfish_amd import _lib, sharding
     spec = G.synthetic_shell(3, 2, nel=4, p=3, jitter=1)
     th, u = G.random_thickness(spec), G.smooth_displacement(spec, 0.5 * spec.h_th)
@@ -198,7 +217,7 @@ def _rank_worker(rank, world, port, q, backend="gloo"):
     S.set_thickness(np.concatenate(th))
     S.set_u(u)
     S.assemble()
-    if backend == "nccl":                                 # bench.py's exchange: device-resident all-gather of the owned residual rows
+    if backend != "gloo":                                 # bench.py's exchange: device-resident all-gather of the owned residual rows
         Rg = sharding.allgather_owned_rows(S.shard, torch.from_numpy(S.D.residual()).cuda(), dist, 3)
         assert np.array_equal(Rg.cpu().numpy(), S.residual())
     rng = np.random.default_rng(11)                       # same seed on every rank: replicated inputs
@@ -235,13 +254,9 @@ def _run_ranks(world, backend):
 
 def test_rccl_sharded_assembly_when_several_gpus_are_visible(oracle_lib):
     """The N > 1 path over RCCL (backend "nccl"): min(device_count, 4) ranks, one GPU each -- residual, products, functionals and
-    the device-resident all-gather of bench.py against the unsharded oracle.  Skips on a one-GPU box (the gloo test below covers
-    the same code with both ranks on GPU 0); on a multi-GPU lease it is the first thing that exercises RCCL."""
-    import torch
-    n = torch.cuda.device_count()                         # does not initialise the GPU in this process
-    if n < 2:
-        pytest.skip("one GPU visible: RCCL needs at least two")
-    _check_sharded_results(_run_ranks(min(n, 4), "nccl"))
+    the device-resident all-gather of bench.py against the unsharded oracle.  On a one-GPU box two ranks share the GPU (_init_ranks: "nccl-one-gpu"):
+    the same device-resident code over RCCL's socket transport."""
+    _check_sharded_results(_run_ranks(*_rccl_world(4)))
 
 
 def test_two_rank_sharded_assembly_on_gpu(oracle_lib):
@@ -1484,13 +1499,7 @@ def test_thickness_opt_group_wired_like_the_reference_demo():
 def _group_rank_worker(rank, world, port, q, backend):
     import torch
     import torch.distributed as dist
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dev = rank if backend == "nccl" else 0               # nccl (= RCCL): one GPU per rank; gloo: every rank on GPU 0
-    if backend == "nccl":
-        torch.cuda.set_device(dev)
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev))
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+    dev = _init_ranks(rank, world, port, backend)
     r = _thickness_opt_group_totals(comm=dist, device=dev)
     if rank == 0:
         q.put(r)
@@ -1533,24 +1542,15 @@ def test_thickness_opt_group_on_a_sharded_problem_two_ranks_one_gpu():
 
 
 def test_thickness_opt_group_on_a_sharded_problem_over_rccl():
-    import torch
-    n = torch.cuda.device_count()
-    if n < 2:
-        pytest.skip("one GPU visible: RCCL needs at least two")
-    _check_sharded_group(_run_group_ranks(min(n, 3), "nccl"))
+    """The sharded ThicknessOptGroup of the test above over RCCL: min(device_count, 3) ranks with a GPU each, two ranks on the GPU of a one-GPU box."""
+    _check_sharded_group(_run_group_ranks(*_rccl_world(3)))
 
 
 def _dist_solver_worker(rank, world, port, q, backend):
     import torch
     import torch.distributed as dist
     from goldfish_amd.nonmatching_opt import NonMatchingOpt
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dev = rank if backend == "nccl" else 0
-    if backend == "nccl":
-        torch.cuda.set_device(dev)
-        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev))
-    else:
-        dist.init_process_group("gloo", rank=rank, world_size=world)
+    dev = _init_ranks(rank, world, port, backend)
     spec = G.synthetic_shell(4, 4, nel=10, p=3, jitter=2)
     nm = NonMatchingOpt.from_spec(spec, comm=dist, device=dev)
     nm.sharded_solver = "distributed"
@@ -1633,12 +1633,8 @@ def test_a_failure_of_the_distributed_solver_on_one_rank_is_every_ranks_failure(
 
 def test_distributed_factorisation_over_rccl():
     """The same on one GPU per rank over RCCL (Schur complements and boundary contributions by all_gather_into_tensor, x by all_reduce on device tensors): runs as
-    soon as two GPUs are visible."""
-    import torch
-    n = torch.cuda.device_count()
-    if n < 2:
-        pytest.skip("one GPU visible: RCCL needs at least two")
-    test_distributed_factorisation_on_a_sharded_problem(min(n, 3), backend="nccl")
+    soon as two GPUs are visible; on a one-GPU box two ranks share the GPU (_init_ranks: "nccl-one-gpu")."""
+    test_distributed_factorisation_on_a_sharded_problem(*_rccl_world(3))
 
 
 @pytest.mark.parametrize("world", [2, 3])
