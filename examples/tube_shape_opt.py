@@ -16,6 +16,9 @@ true K^T solve).  Driven through the operations of goldfish_amd (reduced space):
     gradient   sum_f A_f^T D^T [dW/dCP_f - (dR/dCP_f)^T lam]   D = shopt_dcpsurf_fedcpffd, A_f = shopt_dcpaligndcpffd[f]
 
 Usage: python examples/tube_shape_opt.py
+       python -m torch.distributed.run --nproc-per-node N examples/tube_shape_opt.py   (the patches sharded over N ranks, as the reference runs its demos under
+       mpirun; one GPU per rank, or every rank on GPU 0 over gloo when fewer GPUs are visible; the non-symmetric K is factored across the ranks when the distributed
+       factorisation applies -- GF_SHARDED_SOLVER=distributed forces it for a model this small)
 """
 import os
 import sys
@@ -31,9 +34,9 @@ from goldfish_amd.operations.int_energy_exop import IntEnergyExOperation  # noqa
 from goldfish_amd.utils.ffd_utils import create_3D_block                  # noqa: E402
 
 
-def build(amp=0.06, p=3, nels=((5, 2), (6, 3), (4, 2), (7, 3)), E=1.0e12, pressure=1.0, device=0):
+def build(amp=0.06, p=3, nels=((5, 2), (6, 3), (4, 2), (7, 3)), E=1.0e12, pressure=1.0, device=0, comm=None):
     spec = G.pressurised_tube(nels=nels, p=p, E=E, pressure=pressure, shape=lambda th: 1.0 + 0.5 * amp * (1.0 - np.cos(4.0 * th)))
-    nm = NonMatchingOptFFD.from_spec(spec, device=device, klass=NonMatchingOptFFD)
+    nm = NonMatchingOptFFD.from_spec(spec, device=device, klass=NonMatchingOptFFD, comm=comm)
     nm.set_shopt_surf_inds_FFD([0, 1], [0, 1, 2, 3])
     blk = create_3D_block([2, 2, 1], 3, [list(l) for l in nm.cpsurf_des_lims])
     nm.set_shopt_FFD(blk.knots, blk.control)
@@ -107,8 +110,8 @@ class ReducedShapeProblem:
         return float(r.std()), float(r.mean())
 
 
-def run(maxiter=60, verbose=True, **kw):
-    nm = build(**kw)
+def run(maxiter=60, verbose=True, comm=None, device=0, **kw):
+    nm = build(comm=comm, device=device, **kw)
     prob = ReducedShapeProblem(nm)
     x0 = prob.x0
     w0 = prob.objective(x0)
@@ -121,8 +124,31 @@ def run(maxiter=60, verbose=True, **kw):
     if verbose:
         print("internal energy %.6e -> %.6e (x %.1f smaller), %d iterations, %d state solves" % (w0, w1, w0 / w1, res.nit, prob.n_state_solves))
         print("cross-section radius: mean %.4f -> %.4f, standard deviation %.4f -> %.4f (circle: 0)" % (r0[1], r1[1], r0[0], r1[0]))
+        print("final internal energy %.15e, radius standard deviation %.15e" % (w1, r1[0]))
     return dict(x=res.x, w0=w0, w1=w1, r0=r0, r1=r1, problem=prob, result=res)
 
 
+def main():
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world == 1:
+        run()
+        return
+    import torch
+    import torch.distributed as dist
+    rank, local = int(os.environ["RANK"]), int(os.environ.get("LOCAL_RANK", "0"))
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    if torch.cuda.device_count() >= world:                                # one GPU per rank: RCCL
+        torch.cuda.set_device(local)
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local))
+    else:                                                                 # rehearsal: every rank on GPU 0, exchanges through the host
+        local = 0
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        run(comm=dist, device=local, verbose=rank == 0)
+        dist.barrier()                      # only on the way out of a run that finished: a barrier in ``finally`` turns one rank's exception into a hang of the others
+    finally:
+        dist.destroy_process_group()
+
+
 if __name__ == "__main__":
-    run()
+    main()

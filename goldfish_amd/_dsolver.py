@@ -20,8 +20,12 @@ Distributed: the subtree factorisations and sweeps, the separator fronts (one ra
 rows of S, the x of S, the refinement residuals.  split_tree (round 4's scheme: subtrees of the free dissection dealt by work, K and the top replicated) is kept for
 tools/dist_solver_model.py, which prices both.
 
-K must be symmetric (the general mode of the single-GPU solver is not distributed).  ``dist`` is torch.distributed ('nccl' == RCCL on a multi-GPU node; 'gloo' in
-the tests, where the buffers travel through the host)."""
+A K that is not symmetric (the load stiffness of a follower pressure): ``general=True`` factors the symmetric part (K + K^T) / 2 exactly as a symmetric K is factored
+(gfs_set_general on every partial handle; a rank's handle reads the block of a pair whose partner row is a ghost from the owned row alone: the blocks between control
+points of different ranks are symmetric -- to round-off -- because only the penalty coupling crosses patches and a patch is never split between ranks), and the
+refinement runs against K or K^T with the sharded products -- the rules of the one-GPU general mode.  Several right-hand sides share every exchange: a substitution
+of k columns all-gathers their boundary contributions once per level and all-reduces their x once.  ``dist`` is torch.distributed ('nccl' == RCCL on a multi-GPU
+node; 'gloo' in the tests, where the buffers travel through the host)."""
 import ctypes as C
 
 import numpy as np
@@ -49,6 +53,12 @@ def _bind():
     L.gfs_x_ptr.restype = vp
     L.gfs_forward_dev.argtypes = [vp, vp]
     L.gfs_backward_dev.argtypes = [vp]
+    L.gfs_forward_multi_dev.argtypes = [vp, C.c_int, vp]
+    L.gfs_backward_multi_dev.argtypes = [vp, C.c_int]
+    L.gfs_x_ptr_multi.argtypes = [vp, C.c_int]
+    L.gfs_x_ptr_multi.restype = vp
+    for name in ("gfs_get_fbnd_multi", "gfs_set_fbnd_multi"):
+        getattr(L, name).argtypes = [vp, C.c_int, C.c_int64, _i64p, vp, C.c_int64]
     L._gf_partial_bound = True
     return L
 
@@ -155,9 +165,10 @@ def partial_symbolic(sym, keep, stub_roots=(), later_cp=None):
 class _Part:
     """One partial handle of libgoldfish_solver (gfs_create_nd_partial) over partial_symbolic(...), created in its OWN numbering of the control points:
     ``to_own`` maps a global control point to that numbering (-1: not there), ``own_ids`` the other way; nb_ptr / nb: the control-point graph in that numbering;
-    dK: the K values in the layout of that graph; ``row_ok``: rows that hold values (None: all)."""
+    dK: the K values in the layout of that graph; ``row_ok``: rows that hold values (None: all); ``general``: factor the symmetric part (gfs_set_general, after the
+    row mask: the pairs with a ghost row are marked in the reverse index)."""
 
-    def __init__(self, L, sym, keep, stub_roots, later_cp, own_ids, nb_ptr, nb, dK, device, row_ok=None):
+    def __init__(self, L, sym, keep, stub_roots, later_cp, own_ids, nb_ptr, nb, dK, device, row_ok=None, general=False):
         fronts, sub, pmap = partial_symbolic(sym, keep, stub_roots, later_cp)
         self.fronts, self.local = fronts, {int(t): i for i, t in enumerate(fronts)}
         self.nbnd = np.diff(sub.bnd_off)
@@ -182,20 +193,25 @@ class _Part:
             self._mask = np.ascontiguousarray(row_ok, np.uint8)
             if L.gfs_set_row_mask(h, self._mask.ctypes.data_as(C.c_void_p)):
                 raise RuntimeError(L.gfs_last_error().decode())
+        if general and L.gfs_set_general(h, 1):
+            raise RuntimeError(L.gfs_last_error().decode())
+        self.xv = {}                                             # right-hand side j -> device view of workspace j's x (gfs_x_ptr_multi)
 
 
 class DistributedSolver:
     """K x = b over the ranks of ``dist`` (see the module docstring).  ``dev_model``: the sharded device model (goldfish_amd/sharding.py: ShardedDeviceModel): its
     ``pattern`` gives the GLOBAL control-point graph (symbolic phase only), its local device model (``dev_model.D``) the K this rank assembled, which the rank's
-    handle reads in place."""
+    handle reads in place.  ``general``: K need not be symmetric (see the module docstring); ``max_refine`` then defaults to 40 steps instead of 3, as on one GPU."""
 
     method = "nd-distributed"
+    MAX_RHS = 8                                                  # right-hand sides per substitution (the library's workspaces); more go in rounds
 
-    def __init__(self, dev_model, dist, group=None, coords=None, leaf=128, max_refine=3):
+    def __init__(self, dev_model, dist, group=None, coords=None, leaf=128, max_refine=None, general=False):
         import torch
         self.torch, self.dist, self.group = torch, dist, group
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
-        self.D, self.max_refine = dev_model, max_refine
+        self.general = bool(general)
+        self.D, self.max_refine = dev_model, (40 if self.general else 3) if max_refine is None else int(max_refine)
         self.device = int(dev_model.device)
         self.cuda = dist.get_backend(group) == "nccl"
         L = self.L = _bind()
@@ -226,6 +242,7 @@ class DistributedSolver:
         self.A = self.B = None
         self.rel_residual = self.backward_error = None
         self.rel_residuals = None
+        self.refinement_steps, self.refinement_steps_all = None, None
         self.small_pivot = False
         # Everything from here to the first collective of refactor() can fail on ONE rank only (a rank's fronts are checked against that rank's free memory): the
         # outcome is agreed on before anybody enters a collective, and every rank raises the same kind of error (a rank that fell back to the host
@@ -271,7 +288,7 @@ class DistributedSolver:
         if mine.size:
             lptr, lnb = loc.cp_graph()
             row_ok = np.arange(cols_g.size) < int(dev_model.n_owned_cp)
-            self.A = _Part(L, sym, mine, (), top_cp, cols_g, lptr, lnb, loc.k_values_ptr(), self.device, row_ok=row_ok)
+            self.A = _Part(L, sym, mine, (), top_cp, cols_g, lptr, lnb, loc.k_values_ptr(), self.device, row_ok=row_ok, general=self.general)
         # ---- the separator fronts: ONE RANK EACH (tree-parallel top, round 5).  The fronts of one level of the rank hierarchy are independent, so they are factored side by
         #      side by different ranks (front t by the lowest rank below it) instead of all of them by every rank: the critical path of the top is one front per level
         #      (C4, 8 ranks: 1.84 of 4.07 Tflop; tools/dist_solver_model.py).  Every such front is its own partial handle (the front + stubs for its children) in the
@@ -315,7 +332,8 @@ class DistributedSolver:
         needs_up = [any(sym.parent[t] >= 0 for per in [self.stage_fronts[st]] for ts in per for t in ts) for st in range(self.nstage)]
         self.stage_exchanges = needs_up                              # a stage whose fronts have no parents (the root) sends nothing up
         self.schur_buf = [torch.zeros(self.world * self.schur_pad[st] if needs_up[st] else 1, dtype=torch.float64, device=dev) for st in range(self.nstage)]
-        self.fb_buf = [torch.zeros(self.world * self.fb_pad[st] if needs_up[st] else 1, dtype=torch.float64, device=dev) for st in range(self.nstage)]
+        # boundary contributions of up to MAX_RHS right-hand sides: rank r's slot of a stage holds k columns of fb_pad doubles ([world][k][fb_pad])
+        self.fb_buf = [torch.zeros(self.world * self.MAX_RHS * self.fb_pad[st] if needs_up[st] else 1, dtype=torch.float64, device=dev) for st in range(self.nstage)]
         self.schur_off, self.fb_off = {}, {}                         # front -> offset (doubles) of its slot in its stage's buffer
         for st in range(self.nstage):
             for r, ts in enumerate(self.stage_fronts[st]):
@@ -335,12 +353,11 @@ class DistributedSolver:
             while q >= 0:
                 anc.append(q); q = sym.parent[q]
             later = np.concatenate([sym.elim[sym.elim_off[a]:sym.elim_off[a + 1]] for a in anc]) if anc else None
-            part = _Part(L, sym, [t], kids[t], later, S, sptr, snb, int(self._valB.data_ptr()), self.device)
+            part = _Part(L, sym, [t], kids[t], later, S, sptr, snb, int(self._valB.data_ptr()), self.device, general=self.general)      # full rows of S: no mask
             for c in kids[t]:
                 stc = self.stage_of[c]
                 if L.gfs_set_schur_source(part.h, part.local[c], C.c_void_p(self.schur_buf[stc].data_ptr() + 8 * self.schur_off[c])):
                     raise RuntimeError(L.gfs_last_error().decode())
-            part.x = self._view(L.gfs_x_ptr(part.h), 3 * part.ncp)
             self.T[t] = part
             self.top_elim_s[t] = torch.from_numpy((3 * s_index[sym.elim[sym.elim_off[t]:sym.elim_off[t + 1]]][:, None] + np.arange(3)).ravel()).to(dev)
         self.B = None
@@ -359,7 +376,6 @@ class DistributedSolver:
         self.S_dofs_g = t64(dofs(S))
         here = np.flatnonzero(s_index[cols_g] >= 0)              # local control points that lie in S: the top's x at the boundaries of the own subtrees
         self.S_here_l, self.S_here_s = t64(dofs(here)), t64(dofs(s_index[cols_g[here]]))
-        self.xA = self._view(L.gfs_x_ptr(self.A.h), 3 * self.A.ncp) if self.A else None
         self.b_dev = torch.zeros(self.n, dtype=torch.float64, device=dev)
         # |K|_F from the owned rows of all ranks (the backward error's norm)
         nnz_owned = 9 * int(loc.cp_graph()[0][int(dev_model.n_owned_cp)])
@@ -543,27 +559,52 @@ class DistributedSolver:
                 h_ = ss.cpu(); self.dist.all_reduce(h_, group=self.group); ss = h_
         self.norm_K = float(ss.sqrt())
 
-    def _substitute(self, b_dev):
-        """x = (L D L^T)^-1 b for one right-hand side on the device (torch tensor, replicated); returns a new device tensor (replicated).  Forward: the own subtrees, then
-        the separator fronts level by level upwards (boundary contributions all-gathered per level); backward: the levels downwards (the x of a level summed over the
-        ranks into the replicated x of S), then the own subtrees.  The library calls return when the device is done with them; torch's stream is drained only where the
-        library consumes what torch wrote.  A library error on one rank does not leave the others waiting in a collective: the rank keeps taking part, the failure rides
-        in an extra entry of the all-reduced x, and every rank raises."""
+    def _xv(self, P, j):
+        """Device view of the x of right-hand side j of partial handle P (its workspace j; created by the library on first use)."""
+        v = P.xv.get(j)
+        if v is None:
+            ptr = self.L.gfs_x_ptr_multi(P.h, int(j))
+            if not ptr:
+                raise RuntimeError(self.L.gfs_last_error().decode())
+            v = P.xv[j] = self._view(ptr, 3 * P.ncp)
+        return v
+
+    def _fb_ptr(self, t, j, k):
+        """Address of the boundary contribution of front t for right-hand side j in its stage's buffer when k right-hand sides travel: [world][k][fb_pad]."""
+        st = self.stage_of[t]
+        pad, r = self.fb_pad[st], self.prod_of[t]
+        return self.fb_buf[st].data_ptr() + 8 * (r * k * pad + j * pad + self.fb_off[t] - r * pad)
+
+    def _fb_allgather(self, st, k):
+        if self.stage_exchanges[st] and self.world > 1:
+            pad = k * self.fb_pad[st]
+            self._allgather(self.fb_buf[st][:self.world * pad], pad)
+
+    def _substitute(self, B_dev):
+        """X = (L D L^T)^-1 B for the k <= MAX_RHS rows of the device tensor B ((k, n), replicated); returns a new (k, n) device tensor (replicated).  Forward: the own
+        subtrees, then the separator fronts level by level upwards (the k columns' boundary contributions in ONE all-gather per level); backward: the levels downwards (the
+        x of a level summed over the ranks into the replicated x of S, one all-reduce per level for all columns), then the own subtrees; one all-reduce of the pieces of X.
+        Column j is computed as a substitution of that column alone would compute it (gfs_forward_multi_dev / gfs_backward_multi_dev).  The library calls return when
+        the device is done with them; torch's stream is drained only where the library consumes what torch wrote.  A library error on one rank does not leave the others
+        waiting in a collective: the rank keeps taking part, the failure rides in an extra entry of the all-reduced X, and every rank raises."""
         L, torch = self.L, self.torch
-        st = torch.cuda.current_stream(b_dev.device)
+        k = int(B_dev.shape[0])
+        if not 1 <= k <= self.MAX_RHS:
+            raise ValueError("DistributedSolver._substitute: 1 .. %d right-hand sides, got %d" % (self.MAX_RHS, k))
+        st = torch.cuda.current_stream(B_dev.device)
         err = None
-        bS = b_dev[self.S_dofs_g].contiguous()
+        bS = B_dev[:, self.S_dofs_g].contiguous()
         try:
             if self.A is not None:
-                bl = b_dev[self.loc_dof_g].contiguous()            # the right-hand side in this rank's local numbering
+                bl = B_dev[:, self.loc_dof_g].contiguous()         # the right-hand sides in this rank's local numbering
                 st.synchronize()
-                self._check(L.gfs_forward_dev(self.A.h, C.c_void_p(bl.data_ptr())))
+                self._check(L.gfs_forward_multi_dev(self.A.h, k, C.c_void_p(bl.data_ptr())))
                 if self._rootsA.size:
                     t0 = self.my_roots[0]
-                    self._check(L.gfs_get_fbnd_packed(self.A.h, self._rootsA.size, self._rootsA.ctypes.data_as(_i64p), C.c_void_p(self.fb_buf[0].data_ptr() + 8 * self.fb_off[t0])))
+                    self._check(L.gfs_get_fbnd_multi(self.A.h, k, self._rootsA.size, self._rootsA.ctypes.data_as(_i64p), C.c_void_p(self._fb_ptr(t0, 0, k)), self.fb_pad[0]))
         except RuntimeError as e:
             err = str(e)
-        self._stage_allgather(self.fb_buf, self.fb_pad, 0)
+        self._fb_allgather(0, k)
         for stg in range(1, self.nstage):
             try:
                 st.synchronize()
@@ -572,15 +613,17 @@ class DistributedSolver:
                         continue
                     P = self.T[t]
                     for c in self.top_kids[t]:
-                        self._check(L.gfs_set_fbnd(P.h, P.local[c], C.c_void_p(self.fb_buf[self.stage_of[c]].data_ptr() + 8 * self.fb_off[c])))
-                    self._check(L.gfs_forward_dev(P.h, C.c_void_p(bS.data_ptr())))
+                        fc = np.array([P.local[c]], np.int64)
+                        self._check(L.gfs_set_fbnd_multi(P.h, k, 1, fc.ctypes.data_as(_i64p), C.c_void_p(self._fb_ptr(c, 0, k)), self.fb_pad[self.stage_of[c]]))
+                    self._check(L.gfs_forward_multi_dev(P.h, k, C.c_void_p(bS.data_ptr())))
                     if self.sym.parent[t] >= 0:
-                        self._check(L.gfs_get_fbnd(P.h, P.local[t], C.c_void_p(self.fb_buf[stg].data_ptr() + 8 * self.fb_off[t])))
+                        ft = np.array([P.local[t]], np.int64)
+                        self._check(L.gfs_get_fbnd_multi(P.h, k, 1, ft.ctypes.data_as(_i64p), C.c_void_p(self._fb_ptr(t, 0, k)), self.fb_pad[stg]))
             except RuntimeError as e:
                 err = err or str(e)
-            self._stage_allgather(self.fb_buf, self.fb_pad, stg)
-        # backward: the separator levels from the root down; xS = the replicated x of S
-        xS = torch.zeros(3 * self.S.size, dtype=torch.float64, device=b_dev.device)
+            self._fb_allgather(stg, k)
+        # backward: the separator levels from the root down; xS = the replicated x of S, one row per right-hand side
+        xS = torch.zeros((k, 3 * self.S.size), dtype=torch.float64, device=B_dev.device)
         for stg in range(self.nstage - 1, 0, -1):
             delta = torch.zeros_like(xS)
             try:
@@ -588,10 +631,13 @@ class DistributedSolver:
                     if self.stage_of[t] != stg or err is not None:
                         continue
                     P = self.T[t]
-                    P.x.copy_(xS)                                       # x of the ancestors' control points at this front's boundary
+                    for j in range(k):
+                        self._xv(P, j).copy_(xS[j])                     # x of the ancestors' control points at this front's boundary
                     st.synchronize()
-                    self._check(L.gfs_backward_dev(P.h))
-                    delta[self.top_elim_s[t]] = P.x[self.top_elim_s[t]]
+                    self._check(L.gfs_backward_multi_dev(P.h, k))
+                    idx = self.top_elim_s[t]
+                    for j in range(k):
+                        delta[j, idx] = self._xv(P, j)[idx]
             except RuntimeError as e:
                 err = err or str(e)
             if self.world > 1:
@@ -600,78 +646,119 @@ class DistributedSolver:
                 else:
                     dc = delta.cpu(); self.dist.all_reduce(dc, group=self.group); delta = dc.to(xS.device)
             xS += delta
-        x = torch.zeros(self.n + 1, dtype=torch.float64, device=b_dev.device)
+        n = self.n
+        x = torch.zeros(k * n + 1, dtype=torch.float64, device=B_dev.device)
+        X = x[:k * n].view(k, n)
         try:
             if self.A is not None and err is None:
-                self.xA[self.S_here_l] = xS[self.S_here_s]              # the separators' x at the boundaries of the own subtrees
+                for j in range(k):
+                    self._xv(self.A, j)[self.S_here_l] = xS[j, self.S_here_s]      # the separators' x at the boundaries of the own subtrees
                 st.synchronize()
-                self._check(L.gfs_backward_dev(self.A.h))
-                x[self.own_dofs_g] = self.xA[self.own_dofs_l]
+                self._check(L.gfs_backward_multi_dev(self.A.h, k))
+                for j in range(k):
+                    X[j, self.own_dofs_g] = self._xv(self.A, j)[self.own_dofs_l]
             if self.rank == 0:
-                x[self.S_dofs_g] = xS
+                X[:, self.S_dofs_g] = xS
         except RuntimeError as e:
             err = err or str(e)
-        x[self.n] = 0.0 if err is None else 1.0
+        x[k * n] = 0.0 if err is None else 1.0
         if self.cuda:
             self.dist.all_reduce(x, group=self.group)
         else:
             xc = x.cpu()
             self.dist.all_reduce(xc, group=self.group)
-            x = xc.to(b_dev.device)
-        if float(x[self.n]) > 0.0:
+            x = xc.to(B_dev.device)
+        if float(x[k * n]) > 0.0:
             raise RuntimeError("DistributedSolver: a substitution failed on at least one rank (rank %d%s)" % (self.rank, ": " + err if err else ""))
-        return x[:self.n]
+        return x[:k * n].view(k, n)
 
-    def _residual_dev(self, b, x):
-        """b - K x with the model's global K (collective on a sharded model); device tensors when the model exchanges on the device, else through the host."""
+    def _residual_dev(self, b, x, transpose=False):
+        """b - K x (or b - K^T x) with the model's global K (collective on a sharded model); device tensors when the model exchanges on the device, else through the host."""
         if getattr(self.D, "_tdev", None) is not None and hasattr(self.D, "apply_fwd_dev"):
-            return b - self.D.apply_fwd_dev(0, x)
-        return b - self.torch.from_numpy(self.D.apply(0, x.cpu().numpy())).to(b.device)
+            return b - (self.D.apply_rev_dev(0, x) if transpose else self.D.apply_fwd_dev(0, x))
+        return b - self.torch.from_numpy(self.D.apply(0, x.cpu().numpy(), transpose=transpose)).to(b.device)
+
+    def _solve_block(self, B_dev, transpose, steps):
+        """Up to MAX_RHS right-hand sides refined in lockstep: every round takes the residuals of the columns still being refined and substitutes their corrections in ONE
+        blocked sweep.  A column follows the rule of its single solve -- a step must bring the residual below ``rate`` times the best so far (0.5: gfs_solve's rule for a
+        symmetric K; 0.95 in general mode, where the refinement is the solver for the skew part), else the better of the last two iterates is kept -- so it ends bitwise
+        where its single solve ends.  Returns (x per column as device vectors, residual norms, right-hand side norms, refinement steps per column)."""
+        torch = self.torch
+        k = int(B_dev.shape[0])
+        rate = 0.95 if self.general else 0.5
+        X0 = self._substitute(B_dev)
+        xs = [X0[j].clone() for j in range(k)]                       # vectors of their own: every norm below reads a fresh tensor, as in a single solve
+        bs = [B_dev[j].clone() for j in range(k)]
+        nb_ = [float(torch.linalg.vector_norm(b)) for b in bs]
+        best, prev, its = [None] * k, [None] * k, [0] * k
+        active = list(range(k))
+        for it in range(steps + 1):
+            if not active:
+                break
+            nxt, R = [], []
+            for j in active:
+                r = self._residual_dev(bs[j], xs[j], transpose)
+                nr = float(torch.linalg.vector_norm(r))
+                if best[j] is not None and not nr < rate * best[j]:
+                    if nr >= best[j]:
+                        xs[j] = prev[j]                               # the last correction did not help: keep the previous iterate
+                    else:
+                        best[j] = nr
+                    continue
+                best[j] = nr
+                if it == steps or nr == 0.0:
+                    continue
+                prev[j] = xs[j]
+                nxt.append(j)
+                R.append(r)
+            if nxt:
+                D = self._substitute(torch.stack(R))
+                for i, j in enumerate(nxt):
+                    xs[j] = xs[j] + D[i]
+                    its[j] += 1
+            active = nxt
+        return xs, best, nb_, its
 
     def solve(self, b, transpose=False, max_refine=None):
-        """x = K^-1 b; refinement against K itself while a step halves the residual (gfs_solve's rule), ``max_refine`` steps at most.  b comes in and x goes out as host
-        arrays (the problem surface's replicated vectors); in between everything stays on the device."""
-        torch = self.torch
-        if transpose:
-            raise NotImplementedError("DistributedSolver: K is symmetric here (general mode is single-GPU)")
+        """x = K^-1 b (K^-T b in general mode with ``transpose``): the k = 1 case of solve_multi.  b comes in and x goes out as host arrays (the problem surface's
+        replicated vectors); in between everything stays on the device."""
         b = np.ascontiguousarray(b, float)
-        if b.size != self.n:
+        if b.ndim != 1 or b.size != self.n:
             raise ValueError("DistributedSolver.solve: expected %d values, got %d" % (self.n, b.size))
-        steps = self.max_refine if max_refine is None else int(max_refine)
-        dev = self.b_dev.device
-        with torch.cuda.device(dev):
-            bd = torch.from_numpy(b).to(dev)
-            x = self._substitute(bd)
-            nb_ = float(torch.linalg.vector_norm(bd))
-            best, x_prev = None, None
-            for it in range(steps + 1):
-                r = self._residual_dev(bd, x)
-                nr = float(torch.linalg.vector_norm(r))
-                if best is not None and not nr < 0.5 * best:
-                    if nr >= best:
-                        x = x_prev
-                    else:
-                        best = nr
-                    break
-                best = nr
-                if it == steps or nr == 0.0:
-                    break
-                x_prev = x
-                x = x + self._substitute(r.contiguous())
-            self.rel_residual = best / nb_ if nb_ > 0 else best
-            den = self.norm_K * float(torch.linalg.vector_norm(x)) + nb_
-            self.backward_error = best / den if den > 0 else best
-            return x.cpu().numpy()
+        return self.solve_multi(b[None, :], transpose=transpose, max_refine=max_refine)[0]
 
     def solve_multi(self, B, transpose=False, max_refine=None):
-        B = np.atleast_2d(np.asarray(B, float))
-        X, rr, be = np.empty_like(B), [], 0.0
-        for k in range(B.shape[0]):
-            X[k] = self.solve(B[k], transpose=transpose, max_refine=max_refine)
-            rr.append(self.rel_residual)
-            be = max(be, self.backward_error)
+        """X[j] = K^-1 B[j] (K^-T B[j] in general mode with ``transpose``) for the rows of B: rounds of up to MAX_RHS right-hand sides, each refined in lockstep with
+        blocked substitutions (_solve_block); row j of the result is bitwise what ``solve(B[j])`` returns.  Refinement against K itself (K^T with ``transpose``),
+        ``max_refine`` steps at most (default: the solver's).  ``rel_residuals`` holds one value per row, ``rel_residual`` / ``backward_error`` the largest,
+        ``refinement_steps_all`` the refinement steps per row and ``refinement_steps`` the largest -- the same numbers on every rank."""
+        torch = self.torch
+        B = np.ascontiguousarray(np.atleast_2d(np.asarray(B, float)))
+        if B.ndim != 2 or B.shape[1] != self.n:
+            raise ValueError("DistributedSolver.solve_multi: expected rows of %d values, got %s" % (self.n, B.shape))
+        transpose = bool(transpose) and self.general                   # symmetric K: the same system
+        steps = self.max_refine if max_refine is None else int(max_refine)
+        dev = self.b_dev.device
+        X = np.empty_like(B)
+        rr, be, its = [], [], []
+        with torch.cuda.device(dev):
+            for k0 in range(0, B.shape[0], self.MAX_RHS):
+                Bd = torch.from_numpy(B[k0:k0 + self.MAX_RHS]).to(dev)
+                xs, best, nb_, it = self._solve_block(Bd, transpose, steps)
+                for j, x in enumerate(xs):
+                    X[k0 + j] = x.cpu().numpy()
+                    rr.append(best[j] / nb_[j] if nb_[j] > 0 else best[j])
+                    den = self.norm_K * float(torch.linalg.vector_norm(x)) + nb_[j]
+                    be.append(best[j] / den if den > 0 else best[j])
+                its += it
+            # the decisions above read replicated vectors and agree already; the maxima are agreed on explicitly, so that solve_K accepts or rejects -- a refinement
+            # that stalled included -- on every rank alike
+            m = torch.tensor([max(rr), max(be), float(max(its))], dtype=torch.float64, device=dev if self.cuda else "cpu")
+            if self.world > 1:
+                self.dist.all_reduce(m, op=self.dist.ReduceOp.MAX, group=self.group)
         self.rel_residuals = np.array(rr)
-        self.rel_residual, self.backward_error = float(max(rr)), be
+        self.rel_residual, self.backward_error = float(m[0]), float(m[1])
+        self.refinement_steps_all, self.refinement_steps = np.array(its, np.int64), int(m[2])
         return X
 
     def info(self):

@@ -62,13 +62,20 @@ __device__ __forceinline__ void load_tile(const double* __restrict__ g, double* 
 
 // K (block CSR of libgoldfish_hip, original numbering) -> lower block band in the factorisation order; identity on the padding
 // value of entry ((a, i), (b, j)), b = nb[ptr + k], for the factorisation: K itself, or -- general mode (rev != null: K need not be symmetric) -- its
-// symmetric part (K + K^T) / 2, the transposed entry found through rev[ptr + k] = position of a in b's neighbour list
+// symmetric part (K + K^T) / 2, the transposed entry found through rev[ptr + k] = position of a in b's neighbour list.
+// rev[ptr + k] < 0: b's row is not assembled in this K (a ghost of a rank's handle on a sharded model, gfs_set_row_mask), and a's row alone is used.  That is
+// the symmetric part because the blocks that join control points of different ranks are symmetric: only the penalty coupling joins control points of different
+// patches, a patch is never split between ranks (sharding.partition_patches), and the load stiffness of a follower pressure couples the control points of one patch
+// only.  (K_ab and K_ba^T agree to round-off -- their penalty terms are summed in different orders --, which the refinement against K itself absorbs;
+// tests/test_dsolver_general_cpu.py checks the invariant.)
 __device__ __forceinline__ double fact_value(const double* __restrict__ valK, const long long* __restrict__ nb_ptr, const int* __restrict__ rev, long long ptr, long long deg,
                                              long long k, int b, int i, int j) {
     const double v = valK[9 * ptr + (long long)i * 3 * deg + 3 * k + j];
     if (!rev) return v;
+    const long long kb = rev[ptr + k];
+    if (kb < 0) return v;
     const long long pb = nb_ptr[b], db = nb_ptr[b + 1] - pb;
-    return 0.5 * (v + valK[9 * pb + (long long)j * 3 * db + 3 * (long long)rev[ptr + k] + i]);
+    return 0.5 * (v + valK[9 * pb + (long long)j * 3 * db + 3 * kb + i]);
 }
 __global__ void band_fill_kernel(long long ncp, const long long* __restrict__ nb_ptr, const int* __restrict__ nb, const int* __restrict__ newi, const int* __restrict__ rev,
                                  const double* __restrict__ valK, double* __restrict__ band, const long long* __restrict__ rowoff, long long n, long long npad) {
@@ -1061,13 +1068,17 @@ __global__ __launch_bounds__(256) void residual_t_kernel(long long ncp, const lo
     for (int off = 32; off > 0; off >>= 1) { s0 += __shfl_down(s0, off, 64); s1 += __shfl_down(s1, off, 64); s2 += __shfl_down(s2, off, 64); }
     if (lane == 0) { r[3 * a] = b[3 * a] - s0; r[3 * a + 1] = b[3 * a + 1] - s1; r[3 * a + 2] = b[3 * a + 2] - s2; }
 }
-// reverse index of the (symmetric) block pattern: rev[ptr_a + k] = position of a in the neighbour list of b = nb[ptr_a + k]; -1 (and *bad = 1) if absent
-__global__ void rev_index_kernel(long long nent, long long ncp, const long long* __restrict__ nb_ptr, const int* __restrict__ nb, int* __restrict__ rev, int* __restrict__ bad) {
+// reverse index of the (symmetric) block pattern: rev[ptr_a + k] = position of a in the neighbour list of b = nb[ptr_a + k]; -1 (and *bad = 1) if absent.
+// row_ok (may be nullptr = every row holds values; gfs_set_row_mask): a pair with a row that is not assembled gets -1 and is not a fault -- the lists of a rank's
+// ghost rows are empty or partial, and fact_value then reads the assembled row alone
+__global__ void rev_index_kernel(long long nent, long long ncp, const long long* __restrict__ nb_ptr, const int* __restrict__ nb, int* __restrict__ rev, int* __restrict__ bad,
+                                 const unsigned char* __restrict__ row_ok) {
     const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= nent) return;
     long long lo = 0, hi = ncp - 1;                                   // row a of entry e: last a with nb_ptr[a] <= e
     while (lo < hi) { const long long mid = (lo + hi + 1) >> 1; if (nb_ptr[mid] <= e) lo = mid; else hi = mid - 1; }
     const int a = (int)lo, b = nb[e];
+    if (row_ok && !(row_ok[a] && row_ok[b])) { rev[e] = -1; return; }
     int pos = -1;
     for (long long q = nb_ptr[b]; q < nb_ptr[b + 1]; ++q) if (nb[q] == a) { pos = (int)(q - nb_ptr[b]); break; }
     rev[e] = pos;
@@ -1108,8 +1119,8 @@ __device__ __forceinline__ int nd_pos(const Front& F, int t, int c, const int* _
 // K (block CSR, original numbering) -> fronts: the block (a, b) belongs to the front that eliminates the earlier of the two, and is stored
 // there when a's position is not in front of b's (lower triangle); one wave per control point a
 // row_ok (may be nullptr = every row holds values): a handle on ONE RANK'S K of a sharded model (gfs_set_row_mask) has values in the rows of the control points that
-// rank owns only; the block (a, b) of a pair whose later control point b is a ghost there is then written from a's row, transposed (K is symmetric) -- a rank's
-// subtrees never need a row another rank assembled.
+// rank owns only; the block (a, b) of a pair whose later control point b is a ghost there is then written from a's row, transposed (K is symmetric; in general mode
+// the block of the symmetric part, which a's row alone gives across ranks: fact_value) -- a rank's subtrees never need a row another rank assembled.
 __global__ void nd_scatter_kernel(long long ncp, const long long* __restrict__ nb_ptr, const int* __restrict__ nb, const int* __restrict__ rev, const double* __restrict__ valK,
                                   const Front* __restrict__ fronts, const int* __restrict__ front_of, const long long* __restrict__ order, const int* __restrict__ bnd,
                                   const long long* __restrict__ tri, double* __restrict__ arena, const unsigned char* __restrict__ row_ok) {
@@ -1563,7 +1574,7 @@ struct gfs_handle {
     double *band = nullptr, *linv = nullptr, *dval = nullptr, *wbuf = nullptr, *stat = nullptr;
     double *vb = nullptr, *vy = nullptr, *vz = nullptr, *vx = nullptr, *vr = nullptr, *vsol = nullptr, *vrhs = nullptr, *part = nullptr;
     std::vector<void*> allocs; long long bytes = 0; bool factored = false, small_pivot = false;
-    int* d_rev = nullptr; bool general = false;     // general mode (gfs_set_general): K need not be symmetric
+    int* d_rev = nullptr; int* d_bad = nullptr; bool general = false;     // general mode (gfs_set_general): K need not be symmetric
     long long nnz9 = 0; double normK = 0.0, backward_error = 0.0;     // Frobenius norm of the factored K; backward error of the last solve
     // nested-dissection multifrontal mode
     bool nd = false; std::vector<Front> fronts; std::vector<std::vector<int>> kids; Front* d_fronts = nullptr;
@@ -1598,6 +1609,7 @@ struct gfs_handle {
     // that the sweeps of several right-hand sides (latency-bound chains of small launches) run next to each other (gfs_solve_multi)
     struct SolveWs { hipStream_t stream = nullptr; double *gb = nullptr, *gy = nullptr, *gx = nullptr, *fbnd = nullptr, *sb = nullptr, *sy = nullptr, *sz = nullptr, *sx = nullptr,
                      *vr = nullptr, *vsol = nullptr, *vrhs = nullptr, *part = nullptr; hipGraphExec_t g_solve[3] = {nullptr, nullptr, nullptr};
+                     hipGraphExec_t g_half[2][3] = {};   // partial handles, gfs_forward_multi_dev / gfs_backward_multi_dev: [backward][NR - 1]
                      // round 5: the large fronts of one tree height run side by side on the handle's side streams -- front-local vectors per side stream, fork / join events
                      double* big = nullptr; long long big_len = 0; hipEvent_t ev_fork = nullptr, ev_join[8] = {};
                      double* scratch(int set, int which) const { return set < 0 ? (which == 0 ? sb : which == 1 ? sy : which == 2 ? sz : sx) : big + (size_t)(4 * set + which) * (size_t)big_len; } };
@@ -1916,6 +1928,15 @@ template <int NR> static void nd_backward_all(gfs_handle* h, const gfs_handle::S
         nd_big_join(h, W[0], st, used);
     }
 }
+// NR front-local vectors of up to FUSE_MAX_BLK blocks: more than the 64 KB a launch gets by default
+template <int NR> static void nd_raise_lds(gfs_handle* h) {
+    if (NR == 1 || h->lds_raised[NR - 1]) return;
+    // per handle, not per process: the attribute belongs to the CURRENT DEVICE's copy of the kernel, and a process may hold handles on several GPUs
+    const int lim = 160 * 1024;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nd_fwd_front_kernel<NR>), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nd_bwd_front_kernel<NR>), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
+    h->lds_raised[NR - 1] = true;
+}
 // multifrontal substitutions of NR right-hand sides in one pass over the factors; vectors in the original numbering.  Workspace W[j] holds right-hand side j's vectors;
 // everything runs on W[0]'s stream; the captured graph (the sweeps are ~1e4 launches of fixed structure) belongs to W[0] and is keyed by NR -- the caller always
 // groups the same workspaces (solve_dev_impl: right-hand sides 3 c .. 3 c + NR - 1), so the pointers baked into the graph stay valid.
@@ -1927,15 +1948,7 @@ template <int NR> static void substitute_nd(gfs_handle* h, gfs_handle::SolveWs* 
     hipStream_t st = W[0]->stream;
     for (int j = 0; j < NR; ++j) if (rhs[j]) HIPCHK(hipMemcpyAsync(W[j]->gb, rhs[j], h->n * sizeof(double), hipMemcpyDeviceToDevice, st));
     const gfs_handle::SolveWs* const (&Wc)[NR] = W;
-    if (NR > 1) {                                                                 // NR front-local vectors of up to FUSE_MAX_BLK blocks: more than the 64 KB a launch gets by default
-        // per handle, not per process: the attribute belongs to the CURRENT DEVICE's copy of the kernel, and a process may hold handles on several GPUs
-        if (!h->lds_raised[NR - 1]) {
-            const int lim = 160 * 1024;
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nd_fwd_front_kernel<NR>), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&nd_bwd_front_kernel<NR>), hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-            h->lds_raised[NR - 1] = true;
-        }
-    }
+    nd_raise_lds<NR>(h);
     nd_run_captured(h, &Wm[0]->g_solve[NR - 1], [&] { nd_forward_all<NR>(h, Wc, st); nd_backward_all<NR>(h, Wc, st); }, st);
     for (int j = 0; j < NR; ++j) if (rhs[j]) hipLaunchKernelGGL(nd_out_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, st, h->n, W[j]->gx, x[j], add);
     HIPCHK(hipGetLastError());
@@ -1995,6 +2008,42 @@ static void substitute(gfs_handle* h, const double* rhs, double* x, int add) {
     }
     hipLaunchKernelGGL(permute_out_kernel, dim3(g3), dim3(256), 0, h->stream, h->ncp, h->newi, h->vx, x, add);
     HIPCHK(hipGetLastError());
+}
+
+// The halves for nrhs right-hand sides at once: right-hand side j in workspace j (gfs_x_ptr_multi(h, j), the boundary contributions of gfs_get_fbnd_multi /
+// gfs_set_fbnd_multi), grouped as gfs_solve_multi groups them -- up to RHS_BLOCK per pass over the factors, every group on the stream of its first workspace.
+// Column j is computed in the order of the single-right-hand-side call: x is bitwise what gfs_forward_dev / gfs_backward_dev give.
+template <int NR> static void nd_half_group(gfs_handle* h, int r0, const double* d_B, bool backward) {
+    gfs_handle::SolveWs* Wm[NR];
+    const gfs_handle::SolveWs* W[NR];
+    for (int j = 0; j < NR; ++j) { Wm[j] = &solve_ws(h, r0 + j); W[j] = Wm[j]; }
+    const gfs_handle::SolveWs* const (&Wc)[NR] = W;
+    hipStream_t st = W[0]->stream;
+    nd_raise_lds<NR>(h);
+    if (!backward) {
+        for (int j = 0; j < NR; ++j) HIPCHK(hipMemcpyAsync(W[j]->gb, d_B + (size_t)(r0 + j) * h->n, h->n * sizeof(double), hipMemcpyDeviceToDevice, st));
+        nd_run_captured(h, &Wm[0]->g_half[0][NR - 1], [&] { nd_forward_all<NR>(h, Wc, st); }, st);
+    } else nd_run_captured(h, &Wm[0]->g_half[1][NR - 1], [&] { nd_backward_all<NR>(h, Wc, st); }, st);
+    HIPCHK(hipGetLastError());
+}
+static int half_multi(gfs_handle* h, int nrhs, const double* d_B, bool backward, const char* who) {
+    if (!h || !h->nd || (!backward && !d_B)) return sfail(std::string(who) + ": needs a nested-dissection handle" + (backward ? "" : " and right-hand sides"));
+    if (!h->factored) return sfail(std::string(who) + ": no factorisation (call gfs_refactor)");
+    if (nrhs < 1 || nrhs > gfs_handle::MAX_RHS) return sfail(std::string(who) + ": 1 .. " + std::to_string(gfs_handle::MAX_RHS) + " right-hand sides");
+    constexpr int RB = gfs_handle::RHS_BLOCK;
+    try {
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->stream));                      // the groups' streams start behind the handle's earlier work (factorisation, fbnd copies)
+        for (int r = 0; r < nrhs; ++r) (void)solve_ws(h, r);
+        for (int r0 = 0; r0 < nrhs; r0 += RB) {
+            const int nr = std::min(RB, nrhs - r0);
+            if (nr == 1) nd_half_group<1>(h, r0, d_B, backward);
+            else if (nr == 2) nd_half_group<2>(h, r0, d_B, backward);
+            else nd_half_group<3>(h, r0, d_B, backward);
+        }
+        for (int r0 = 0; r0 < nrhs; r0 += RB) HIPCHK(hipStreamSynchronize(solve_ws(h, r0).stream));
+    } catch (const std::exception& ex) { return sfail(ex.what()); }
+    return 0;
 }
 
 extern "C" {
@@ -2301,6 +2350,7 @@ void gfs_destroy(gfs_handle* h) {
     if (h->g_bwd) (void)hipGraphExecDestroy(h->g_bwd);
     for (size_t k = 0; k < h->ws.size(); ++k) {
         for (auto& g : h->ws[k].g_solve) if (g) (void)hipGraphExecDestroy(g);
+        for (auto& gh : h->ws[k].g_half) for (auto& g : gh) if (g) (void)hipGraphExecDestroy(g);
         if (k > 0 && h->ws[k].stream) (void)hipStreamDestroy(h->ws[k].stream);
         if (h->ws[k].ev_fork) (void)hipEventDestroy(h->ws[k].ev_fork);
         for (auto& e : h->ws[k].ev_join) if (e) (void)hipEventDestroy(e);
@@ -2387,21 +2437,25 @@ int gfs_refactor(gfs_handle* h) {
     return 0;
 }
 
+// the reverse index of general mode under the handle's current row mask (rebuilt by gfs_set_row_mask when the mask changes)
+static void build_rev_index(gfs_handle* h) {
+    long long nent = 0;
+    HIPCHK(hipMemcpy(&nent, h->nb_ptr + h->ncp, sizeof(long long), hipMemcpyDeviceToHost));
+    if (!h->d_rev) h->d_rev = h->dalloc<int>((size_t)nent);
+    if (!h->d_bad) h->d_bad = h->dalloc<int>(1);
+    int bad = 0;
+    HIPCHK(hipMemsetAsync(h->d_bad, 0, sizeof(int), h->stream));
+    if (nent > 0) hipLaunchKernelGGL(rev_index_kernel, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, h->stream, nent, h->ncp, h->nb_ptr, h->nb, h->d_rev, h->d_bad, h->d_row_ok);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&bad, h->d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (bad) throw std::runtime_error("gfs_set_general: the block pattern of K is not symmetric");
+}
 int gfs_set_general(gfs_handle* h, int nonsymmetric) {
     if (!h) return sfail("gfs_set_general: null handle");
     try {
         HIPCHK(hipSetDevice(h->device));
-        if (nonsymmetric && !h->d_rev) {
-            long long nent = 0;
-            HIPCHK(hipMemcpy(&nent, h->nb_ptr + h->ncp, sizeof(long long), hipMemcpyDeviceToHost));
-            h->d_rev = h->dalloc<int>((size_t)nent);
-            int* d_bad = h->dalloc<int>(1); int bad = 0;
-            HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), h->stream));
-            hipLaunchKernelGGL(rev_index_kernel, dim3((unsigned)((nent + 255) / 256)), dim3(256), 0, h->stream, nent, h->ncp, h->nb_ptr, h->nb, h->d_rev, d_bad);
-            HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            if (bad) throw std::runtime_error("gfs_set_general: the block pattern of K is not symmetric");
-        }
+        if (nonsymmetric && !h->d_rev) build_rev_index(h);
         if (h->general != (nonsymmetric != 0)) h->factored = false;       // the factors belong to the other mode
         h->general = nonsymmetric != 0;
     } catch (const std::exception& ex) { return sfail(ex.what()); }
@@ -2613,25 +2667,35 @@ int gfs_set_schur_source(gfs_handle* h, int64_t front, const double* d_buf) {
     return 0;
 }
 // boundary contributions of root fronts: `n` fronts packed one after the other (3 doubles per boundary control point, in the order of each front's boundary list);
-// asynchronous copies on the handle's sweep stream, one synchronisation per call
-static int fbnd_copy(gfs_handle* h, int64_t n, const int64_t* fronts, double* d_buf, bool get, const char* who) {
+// right-hand side j (workspace j) at d_buf + j * ld; asynchronous copies on the handle's sweep stream, one synchronisation per call
+static int fbnd_copy(gfs_handle* h, int64_t n, const int64_t* fronts, double* d_buf, bool get, const char* who, int nrhs = 1, int64_t ld = 0) {
     if (!h || !h->nd) return sfail(std::string(who) + ": needs a nested-dissection handle");
     if (!h->partial) return sfail(std::string(who) + ": needs a partial handle (gfs_create_nd_partial)");
     if (!d_buf || (n > 0 && !fronts)) return sfail(std::string(who) + ": null argument");
     if (get && !h->factored) return sfail(std::string(who) + ": no factorisation (call gfs_refactor)");
-    for (int64_t k = 0; k < n; ++k) if (fronts[k] < 0 || fronts[k] >= (int64_t)h->fronts.size()) return sfail(std::string(who) + ": front index out of range");
+    if (nrhs < 1 || nrhs > gfs_handle::MAX_RHS) return sfail(std::string(who) + ": 1 .. " + std::to_string(gfs_handle::MAX_RHS) + " right-hand sides");
+    size_t total = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        if (fronts[k] < 0 || fronts[k] >= (int64_t)h->fronts.size()) return sfail(std::string(who) + ": front index out of range");
+        total += (size_t)3 * h->fronts[fronts[k]].nb_cp;
+    }
+    if (nrhs > 1 && ld < (int64_t)total) return sfail(std::string(who) + ": the stride of the right-hand sides is shorter than their packed contributions");
     try {
         HIPCHK(hipSetDevice(h->device));
         gfs_handle::SolveWs& W0 = solve_ws(h, 0);
-        size_t off = 0;
-        for (int64_t k = 0; k < n; ++k) {
-            const Front& F = h->fronts[fronts[k]];
-            const size_t len = (size_t)3 * F.nb_cp;
-            if (len) {
-                if (get) HIPCHK(hipMemcpyAsync(d_buf + off, W0.fbnd + 3 * F.bnd_off, len * sizeof(double), hipMemcpyDeviceToDevice, W0.stream));
-                else HIPCHK(hipMemcpyAsync(W0.fbnd + 3 * F.bnd_off, d_buf + off, len * sizeof(double), hipMemcpyDeviceToDevice, W0.stream));
+        for (int j = 0; j < nrhs; ++j) {
+            const gfs_handle::SolveWs& Wj = solve_ws(h, j);
+            double* buf = d_buf + (size_t)j * (size_t)ld;
+            size_t off = 0;
+            for (int64_t k = 0; k < n; ++k) {
+                const Front& F = h->fronts[fronts[k]];
+                const size_t len = (size_t)3 * F.nb_cp;
+                if (len) {
+                    if (get) HIPCHK(hipMemcpyAsync(buf + off, Wj.fbnd + 3 * F.bnd_off, len * sizeof(double), hipMemcpyDeviceToDevice, W0.stream));
+                    else HIPCHK(hipMemcpyAsync(Wj.fbnd + 3 * F.bnd_off, buf + off, len * sizeof(double), hipMemcpyDeviceToDevice, W0.stream));
+                }
+                off += len;
             }
-            off += len;
         }
         HIPCHK(hipStreamSynchronize(W0.stream));
     } catch (const std::exception& ex) { return sfail(ex.what()); }
@@ -2643,9 +2707,12 @@ int gfs_set_row_mask(gfs_handle* h, const unsigned char* mask) {
     if (!h || !h->nd) return sfail("gfs_set_row_mask: needs a nested-dissection handle");
     try {
         HIPCHK(hipSetDevice(h->device));
-        if (!mask) { h->d_row_ok = nullptr; h->factored = false; return 0; }
-        if (!h->d_row_ok) h->d_row_ok = h->dalloc<unsigned char>((size_t)h->ncp);
-        HIPCHK(hipMemcpy(h->d_row_ok, mask, (size_t)h->ncp, hipMemcpyHostToDevice));
+        if (!mask) h->d_row_ok = nullptr;
+        else {
+            if (!h->d_row_ok) h->d_row_ok = h->dalloc<unsigned char>((size_t)h->ncp);
+            HIPCHK(hipMemcpy(h->d_row_ok, mask, (size_t)h->ncp, hipMemcpyHostToDevice));
+        }
+        if (h->d_rev) build_rev_index(h);                 // general mode: the pairs with a ghost row are marked in the reverse index
         h->factored = false;
     } catch (const std::exception& ex) { return sfail(ex.what()); }
     return 0;
@@ -2684,6 +2751,20 @@ int gfs_backward_dev(gfs_handle* h) {
         HIPCHK(hipStreamSynchronize(W0.stream));
     } catch (const std::exception& ex) { return sfail(ex.what()); }
     return 0;
+}
+
+int gfs_forward_multi_dev(gfs_handle* h, int nrhs, const double* d_B) { return half_multi(h, nrhs, d_B, false, "gfs_forward_multi_dev"); }
+int gfs_backward_multi_dev(gfs_handle* h, int nrhs) { return half_multi(h, nrhs, nullptr, true, "gfs_backward_multi_dev"); }
+double* gfs_x_ptr_multi(gfs_handle* h, int rhs) {
+    if (!h || !h->nd || rhs < 0 || rhs >= gfs_handle::MAX_RHS) { sfail("gfs_x_ptr_multi: needs a nested-dissection handle and 0 <= rhs < " + std::to_string(gfs_handle::MAX_RHS)); return nullptr; }
+    try {
+        HIPCHK(hipSetDevice(h->device));
+        return solve_ws(h, rhs).gx;
+    } catch (const std::exception& ex) { sfail(ex.what()); return nullptr; }
+}
+int gfs_get_fbnd_multi(gfs_handle* h, int nrhs, int64_t n, const int64_t* fronts, double* d_out, int64_t ld) { return fbnd_copy(h, n, fronts, d_out, true, "gfs_get_fbnd_multi", nrhs, ld); }
+int gfs_set_fbnd_multi(gfs_handle* h, int nrhs, int64_t n, const int64_t* fronts, const double* d_in, int64_t ld) {
+    return fbnd_copy(h, n, fronts, const_cast<double*>(d_in), false, "gfs_set_fbnd_multi", nrhs, ld);
 }
 
 int gfs_info(gfs_handle* h, double info[8]) {

@@ -535,9 +535,10 @@ class NonMatchingOpt:
                     # a follower pressure's K is not symmetric: the device solver then factors its symmetric part and refines against K / K^T
                     coords = np.stack([self.cp_iga[f] / w for f in range(3)], 1)
                     if self._use_distributed_solver():
-                        # sharded problem, stage 2 (goldfish_amd/_dsolver.py): every rank factors the subtrees dealt to it, the top of the elimination tree is replicated
+                        # sharded problem, stage 2 (goldfish_amd/_dsolver.py): every rank factors the subtrees dealt to it, the top of the elimination tree is replicated;
+                        # a follower pressure's K: the symmetric part is factored across the ranks, the refinement runs against K / K^T (general mode)
                         from . import _dsolver
-                        self._dsolver = _dsolver.DistributedSolver(self.dev, self._dist, self._group, coords=coords)
+                        self._dsolver = _dsolver.DistributedSolver(self.dev, self._dist, self._group, coords=coords, general=not self.symmetric_K)
                     else:
                         self._dsolver = _solver.DeviceSolver(self.dev, coords=coords, general=not self.symmetric_K)
                     self._dsolver_version = ver
@@ -595,8 +596,8 @@ class NonMatchingOpt:
                                "NonMatchingOpt(..., comm=torch.distributed) on a multi-GPU node (goldfish_amd/_dsolver.py; C5 fits 8 x 288 GB); preconditioned CG was "
                                "measured and does not converge on these tangents (goldfish_amd/_krylov.py, profiles/r05_krylov_study.txt)." % (why, self.vec_iga_dof, self.host_solve_max_dofs))
 
-    #: direct solves of a sharded problem: "distributed" (stage 2: subtrees of the elimination tree per rank, replicated top; symmetric K, models large enough
-    #: for the nested-dissection mode), "replicated" (stage 1: every rank factors the gathered K), "auto": distributed when it applies
+    #: direct solves of a sharded problem: "distributed" (stage 2: subtrees of the elimination tree per rank, separator fronts one rank each; a non-symmetric K in
+    #: general mode), "replicated" (stage 1: every rank factors the gathered K), "auto": distributed for models large enough for the nested-dissection mode
     sharded_solver = os.environ.get("GF_SHARDED_SOLVER", "auto")
 
     #: Newton loop: reuse the factorisation for chord steps while they contract (False: the reference's iteration, a factorisation per step -- the default; True;
@@ -611,7 +612,7 @@ class NonMatchingOpt:
 
     def _use_distributed_solver(self):
         from . import _solver
-        if getattr(self, "_dist", None) is None or self.sharded_solver == "replicated" or not self.symmetric_K or getattr(self, "world", 2) < 2:
+        if getattr(self, "_dist", None) is None or self.sharded_solver == "replicated" or getattr(self, "world", 2) < 2:
             return False
         return self.sharded_solver == "distributed" or self.vec_iga_dof // 3 >= _solver.ND_MIN_CP
 

@@ -416,6 +416,23 @@ class ShardedDeviceModel:
             self._apply_dev(which, False, xg[self._loc_dof_g if which == _lib.MAT_K else self._loc_cp_g].contiguous(), y)
             return allgather_owned_rows(self.shard, y, self.dist, 3, group=self.group).clone()
 
+    def apply_rev_dev(self, which, xg):
+        """K^T x for a replicated global device tensor ``xg``: the replicated global result as a device tensor (the local transposed product of the owned rows,
+        whose columns are the local dofs -- owned and ghost --, scattered to global ids, ONE all-reduce; nothing touches the host under RCCL).  What the distributed
+        solver's refinement uses for K^T x = b (a follower pressure makes K non-symmetric)."""
+        import torch
+        _lib = self._lib
+        if which != _lib.MAT_K:
+            raise ValueError("apply_rev_dev: K only (the reverse products of dR/dCP and dR/dh go through apply_many)")
+        with torch.cuda.device(self._tdev):
+            xl = xg[self._loc_dof_g].contiguous()
+            xl[3 * self.n_owned_cp:] = 0.0                                  # ghost rows are not assembled here
+            y = torch.zeros(self.A.ndof, dtype=torch.float64, device=self._tdev)
+            self._apply_dev(which, True, xl, y)
+            out = torch.zeros(self.ndof, dtype=torch.float64, device=self._tdev)
+            out.index_add_(0, self._loc_dof_g, y)                           # local columns -> global ids (distinct: one term per entry)
+            return self._allreduce_dev(out)
+
     def apply_many(self, which, xs, ys, transpose=False):
         """DeviceModel.apply_many with replicated global vectors: transpose=False: ys[0] += sum_m A_m xs[m]; transpose=True: ys[m] += A_m^T xs[0].
         ONE collective per call (DispImOpeartion.apply_linear_fwd / _rev, disp_imop.py:58-128): forward, the local products are summed on the device and the

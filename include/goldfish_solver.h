@@ -107,6 +107,18 @@ double* gfs_x_ptr(gfs_handle* h);
 int gfs_set_row_mask(gfs_handle* h, const unsigned char* mask);
 int gfs_forward_dev(gfs_handle* h, const double* d_b);
 int gfs_backward_dev(gfs_handle* h);
+/* The halves for 1 <= nrhs <= 8 right-hand sides at once (goldfish_amd/_dsolver.py: one exchange per level for all of them).  d_B: nrhs vectors of 3 * ncp doubles one
+ * after the other (device).  Right-hand side j uses the handle's workspace j: its x at gfs_x_ptr_multi(h, j) (j = 0: gfs_x_ptr), its boundary contributions through
+ * gfs_get_fbnd_multi / gfs_set_fbnd_multi (the packed layout of gfs_get_fbnd_packed, right-hand side j at d_buf + j * ld).  Grouped as in gfs_solve_multi: up to three
+ * right-hand sides share one pass over the factors, the groups run on their own streams; every column is computed in the order of the single-right-hand-side call, so x
+ * is bitwise what gfs_forward_dev / gfs_backward_dev give.  Both calls return when the device is done.  General mode (gfs_set_general) on a handle with a row mask: a pair
+ * whose partner row is not assembled takes the block of the symmetric part from the assembled row alone -- on a sharded model the blocks between control points of
+ * different ranks are symmetric (penalty coupling only; a patch is never split between ranks), to round-off, which the refinement against K absorbs. */
+int gfs_forward_multi_dev(gfs_handle* h, int nrhs, const double* d_B);
+int gfs_backward_multi_dev(gfs_handle* h, int nrhs);
+double* gfs_x_ptr_multi(gfs_handle* h, int rhs);
+int gfs_get_fbnd_multi(gfs_handle* h, int nrhs, int64_t n, const int64_t* fronts, double* d_out, int64_t ld);
+int gfs_set_fbnd_multi(gfs_handle* h, int nrhs, int64_t n, const int64_t* fronts, const double* d_in, int64_t ld);
 /* info[0] = half bandwidth (dofs), [1] = block columns, [2] = band tiles per block row, [3] = device bytes,
  * [4] = flops of one factorisation, [5] = 1 if the last factorisation met a pivot below 1e-14 * max |diag|, else 0,
  * [6] = normwise backward error |b - K x| / (|K|_F |x| + |b|) of the last solve (what a backward-stable solve keeps at round-off
